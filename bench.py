@@ -8,7 +8,12 @@ fs 50 Hz), features {mean, var, skewness, kurtosis, zero-crossings} per axis, fl
 feature rows (the reference's rolling_apply output dtype, windows.py:89).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5]
-                    [--strong]
+                    [--strong] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line. --full adds what
+takes runs of its own: the `cpu_baseline` leg (the CPU oracle timed on the host cores).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see
+dump_outputs).
 
 N > 1: one process per GPU. Launched under torch.distributed.run (WORLD_SIZE set) it runs
 as that rank and checks WORLD_SIZE == N; launched plainly it starts N ranks itself
@@ -330,6 +335,32 @@ def load_traffic(config, plan, windows, features):
     return rec.get("bytes_per_launch")
 
 
+DUMP_BUDGET_BYTES = 48 << 20    # of the 64 MB a dump may take in all (every rank's share)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirname, name, t, axis, rank=0, world=1):
+    """--dump-outputs: write what the timed path returned in its last step, the tensor ``t``,
+    as DIR/<name>.npy (DIR/<name>_rank<r>.npy with more than one rank) in its own dtype
+    (float32 or float64). An output larger than this rank's share of DUMP_BUDGET_BYTES is
+    sampled along ``axis`` (windows, or samples of a filtered record): index 0 (the serial
+    row-0 numerics) and a sorted draw without replacement from a generator seeded with
+    DUMP_SEED, so two runs with the same arguments write the same entries. The inputs are
+    the counter-based synthetic record (synth_device, fixed seed): identical from run to
+    run."""
+    assert t.dtype in (torch.float32, torch.float64)
+    os.makedirs(dirname, exist_ok=True)
+    n = t.shape[axis]
+    per = max(1, t.numel() // max(1, n)) * t.element_size()     # bytes per index of `axis`
+    keep = max(1, (DUMP_BUDGET_BYTES // world) // per)
+    if keep < n:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+        pick[0] = 0
+        t = t.index_select(axis, torch.from_numpy(pick).to(t.device))
+    fname = name if world == 1 else "%s_rank%d" % (name, rank)
+    np.save(os.path.join(dirname, fname + ".npy"), np.ascontiguousarray(t.cpu().numpy()))
+
+
 def launch_ranks(n):
     """Run this script as N ranks of ``torch.distributed.run`` on this node (master on
     127.0.0.1, a free port) with the same arguments; returns the launcher's exit code."""
@@ -380,6 +411,8 @@ def run_filtfilt(args, rank, world, device, dist):
 
     elapsed = _timed(timed_steps, 1, dist, device)
     kernel_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in ev]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "filtered", out, 0, rank, world)
     bytes_launch = n * C * (4 + 8 + 16)
     achieved = bytes_launch / (kernel_ms * 1e-3) / 1e9
     # the per-lane kernel (opt-out, other channel counts) has no committed PMC pass
@@ -403,7 +436,7 @@ def run_filtfilt(args, rank, world, device, dist):
                          "algorithmic_bytes_per_launch": bytes_launch, "kernel_ms": kernel_ms},
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_filtfilt(cfg, b, a, zi)
         print(json.dumps(res), flush=True)
 
@@ -507,6 +540,8 @@ def run_strong(args, rank, world, device, dist):
     for _ in range(args.warmup):
         step()
     elapsed = _timed(step, args.steps, dist, device)
+    if args.dump_outputs and rank == 0:     # the gathered rows, as the caller on rank 0 gets them
+        dump_outputs(args.dump_outputs, "features", state["rows"], 2)
     phases = {name: _timed(fn, args.steps, dist, device) * 1e3 / args.steps
               for name, fn in (("scatter_ms", scatter), ("compute_ms", compute),
                                ("gather_ms", gather))}
@@ -696,7 +731,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--out-dtype", default="f64", choices=["f64", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the cpu_baseline leg (the "
+                         "CPU oracle on the host cores); a plain run only times the steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed as "
+                         "DIR/<name>.npy (float32 / float64, a fixed seeded sample of a large "
+                         "output)")
     ap.add_argument("--windows", type=int, default=0, help="override windows per rank")
     ap.add_argument("--features", default="",
                     help="diagnostics: comma-separated feature names replacing the config's")
@@ -714,6 +757,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # self-launch: N fresh rank processes, started before this process touches the GPU
         # (it only waits for them; rank 0 prints the JSON line to the inherited stdout)
@@ -833,6 +878,8 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    if args.dump_outputs:       # this rank's (C, F, nw) rows of the last timed step
+        dump_outputs(args.dump_outputs, "features", out, 2, rank, world)
 
     # the same steps followed by the feature-row gather to rank 0 over RCCL (SURVEY §8e:
     # "with and without the gather"); N = 1 has nothing to gather
@@ -924,7 +971,7 @@ def main():
             # roofline becomes the work rate against the VALU peak; the HBM figures stay
             res["roofline_hbm"] = res["roofline"]
             res["roofline"] = valu
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(res), flush=True)
     if dist:

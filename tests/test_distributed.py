@@ -172,3 +172,43 @@ def test_bench_strong_mode_collectives_on_cpu():
     assert ph["scatter_bytes_from_rank0"] == 4 * ((19999 * 128 + 1024) - 10000 * 128)
     assert ph["gather_bytes_to_rank0"] == 10000 * 2 * 8
     assert res["value"] > 0 and "dry_run" in res
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): an output within the budget is written whole in
+    its own dtype; a larger one as a fixed sample along the window axis (index 0 first,
+    sorted, the same entries on every call) that fits the budget; ranks of a multi-rank run
+    write one file each."""
+    import bench
+    t = torch.arange(3 * 5 * 1000, dtype=torch.float64).reshape(3, 5, 1000)
+    bench.dump_outputs(str(tmp_path), "features", t, 2)
+    a = np.load(tmp_path / "features.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, t.numpy())
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 3 * 5 * 4 * 100)    # 100 windows of float32
+    t32 = t.float()
+    bench.dump_outputs(str(tmp_path / "a"), "features", t32, 2)
+    bench.dump_outputs(str(tmp_path / "b"), "features", t32.clone(), 2)
+    a, b = np.load(tmp_path / "a" / "features.npy"), np.load(tmp_path / "b" / "features.npy")
+    assert a.dtype == np.float32 and a.shape == (3, 5, 100) and np.array_equal(a, b)
+    w = a[0, 0].astype(np.int64)               # row (0, 0) holds the window index itself
+    assert w[0] == 0 and (np.diff(w) > 0).all() and w[-1] < 1000
+    assert np.array_equal(a, t32.numpy()[:, :, w])
+
+    bench.dump_outputs(str(tmp_path / "r"), "features", t32, 2, rank=1, world=2)
+    r = np.load(tmp_path / "r" / "features_rank1.npy")
+    assert r.shape == (3, 5, 50)
+
+
+def test_bench_arguments_full_and_steps():
+    """--steps 0 is rejected (the timed loop runs exactly --steps steps); --full and
+    --dump-outputs parse beside the driver's arguments."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--full", "--dump-outputs", "unused", "--launch-check"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]

@@ -154,7 +154,7 @@ case "${1:-}" in
     # the final lane-walk settings: whole GPU suite, smoke, default bench, lane-walk workloads
     run tests_gpu 1000 - python -u -m pytest -x -q --timeout 300 --timeout-method thread -p no:cacheprovider -m gpu tests
     run smoke 300 - python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')"
-    run bench_default 400 - python bench.py
+    run bench_default 400 - python bench.py --full
     for i in 1 2; do
       run vidx_$i 300 - $B --config cfgidx --steps 10 --warmup 2
       run vgen_$i 300 MHF_FORCE_GENERIC=1 $B --config cfg2 --steps 5 --warmup 1 --windows 200000

@@ -18,7 +18,7 @@ step() {  # step <name> <timeout-s> <cmd...>
 step build 600 python -c "import __graft_entry__ as g; g.build()"
 step pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py --steps 10 --warmup 2 ${BENCH_ARGS:-}
+step bench 600 python bench.py --full --steps 10 --warmup 2 ${BENCH_ARGS:-}
 if [ "${DIST_REHEARSAL:-0}" = "1" ]; then
   # 2 ranks sharing the one GPU, gloo: exercises bench.py's N>1 path (barrier, max-over-ranks)
   step bench_dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \

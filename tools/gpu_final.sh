@@ -13,7 +13,7 @@ step() {  # step <name> <timeout-s> <cmd...>
   if [ $rc -ne 0 ]; then exit $rc; fi
 }
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')"
-step bench_default 400 python bench.py
+step bench_default 400 python bench.py --full
 step bench_gloo2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 1 --backend gloo --no-cpu-baseline
 for c in ${CONFIGS:-cfg3 cfg5}; do
   step bench_$c 300 python bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline

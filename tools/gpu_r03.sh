@@ -17,7 +17,7 @@ if [ -n "${TESTS:-}" ]; then step tests_new 900 $PYT -m gpu $TESTS; fi
 if [ "${FULL:-1}" = "1" ]; then step tests_gpu 1000 $PYT -m gpu tests; fi
 if [ "${SMOKE:-1}" = "1" ]; then step smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')"; fi
 if [ "${BENCH:-1}" = "1" ]; then
-  step bench_default 400 python bench.py
+  step bench_default 400 python bench.py --full
   step bench_gpus2 300 python bench.py --gpus 2 --steps 5 --warmup 1 --backend gloo --no-cpu-baseline
 fi
 for c in ${CONFIGS:-}; do

@@ -17,7 +17,7 @@ PYT="python -u -m pytest -x -v --timeout 300 --timeout-method thread -p no:cache
 step tests_div 600 $PYT -m gpu tests/test_gpu_parity.py -k "division"
 step tests_gpu 1000 $PYT -m gpu tests
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')"
-step bench_default 400 python bench.py
+step bench_default 400 python bench.py --full
 step bench_gpus2 300 python bench.py --gpus 2 --steps 5 --warmup 1 --backend gloo --no-cpu-baseline
 for c in ${CONFIGS:-cfg3 cfg4 cfg5 cfg2f64 cfgidx}; do
   step bench_$c 300 python bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline

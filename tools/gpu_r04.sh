@@ -25,7 +25,7 @@ case "${1:-}" in
     # smoke, the default bench, the strong-scaling pipeline (N = 1 RCCL, N = 2 gloo rehearsal)
     run tests_gpu 1000 - $PYT tests
     run smoke 300 - python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')"
-    run bench_default 400 - python bench.py
+    run bench_default 400 - python bench.py --full
     run strong1_cfg5 300 - $B --strong --config cfg5 --steps 5 --warmup 1
     run strong1_cfg2 300 - $B --strong --config cfg2 --steps 5 --warmup 1
     run strong2_gloo_cfg5 300 - $B --gpus 2 --backend gloo --strong --config cfg5 --windows 200000 --steps 3 --warmup 1
@@ -59,9 +59,9 @@ case "${1:-}" in
   f8)
     # §8f kernels measured on their own: bench lines, then rocprofv3 kernel
     # trace + PMC passes (tools/profile.sh) for each, and the cfgidx traffic refresh
-    run bench_filt 300 - python bench.py --config filt --steps 5 --warmup 1
-    run bench_cfg2med 300 - python bench.py --config cfg2med --steps 10 --warmup 2
-    run bench_sampen256 300 - python bench.py --config sampen256 --steps 5 --warmup 1
+    run bench_filt 300 - python bench.py --full --config filt --steps 5 --warmup 1
+    run bench_cfg2med 300 - python bench.py --full --config cfg2med --steps 10 --warmup 2
+    run bench_sampen256 300 - python bench.py --full --config sampen256 --steps 5 --warmup 1
     run prof_filt 600 "KRE=iir_chunk_kernel" bash tools/profile.sh r04d_filt --config filt --steps 3 --warmup 1
     run prof_cfg2med 600 "KRE=order_kernel" bash tools/profile.sh r04d_cfg2med --config cfg2med --steps 5 --warmup 1
     run prof_sampen 600 "KRE=sampen_kernel" bash tools/profile.sh r04d_sampen256 --config sampen256 --steps 3 --warmup 1

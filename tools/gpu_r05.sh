@@ -51,7 +51,7 @@ case "${1:-}" in
     # the whole GPU suite at HEAD, smoke, then one bench line per workload
     run tests_gpu 900 - python -u -m pytest -x -q --timeout 300 --timeout-method thread -p no:cacheprovider -m gpu tests
     run smoke 300 - python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')"
-    run bench_default 400 - python bench.py
+    run bench_default 400 - python bench.py --full
     for c in cfg3 cfg4 cfg5 cfgidx ovl250 cfg2med cfg2ord sampen256 cfg2f64 cfg3f64; do
       run bench_$c 300 - $B --config $c --steps 10 --warmup 2
     done
@@ -187,7 +187,7 @@ case "${1:-}" in
   fin)
     run tests_gpu 900 - python -u -m pytest -x -q --timeout 300 --timeout-method thread -p no:cacheprovider -m gpu tests
     run smoke 300 - python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')"
-    run bench_default 400 - python bench.py
+    run bench_default 400 - python bench.py --full
     run bench_cfg2med 300 - $B --config cfg2med --steps 10 --warmup 2
     run bench_cfg2ord 300 - $B --config cfg2ord --steps 10 --warmup 2
     QUICK=1 run prof_q_cfg2med 300 "KRE=order_" bash tools/profile.sh r05r_cfg2med --config cfg2med --steps 3 --warmup 1

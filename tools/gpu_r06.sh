@@ -132,9 +132,9 @@ case "${1:-}" in
     run tests_gpu 900 - $PYTNX tests
     if grep -q "illegal memory access" gpurun_out/tests_gpu.log; then echo "FAULT in suite"; exit 3; fi
     SOFT=0
-    run bench_default 300 - python bench.py
+    run bench_default 300 - python bench.py --full
     for c in cfg3 cfg4 cfg5; do
-      run bench_$c 400 - python bench.py --config $c --steps 10 --warmup 2
+      run bench_$c 400 - python bench.py --full --config $c --steps 10 --warmup 2
     done
     qprof r06c_cfg4 tile_kernel --config cfg4 --plan tile_w256_c3 -- --config cfg4 --steps 3 --warmup 1
     qprof r06c_cfg5 spectral_reg --config cfg5 --plan spectral_reg -- --config cfg5 --steps 5 --warmup 1
@@ -224,14 +224,14 @@ PY
     if grep -q "illegal memory access" gpurun_out/tests_gpu.log; then echo "FAULT in suite"; exit 3; fi
     SOFT=0
     run smoke 300 - python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')"
-    run bench_default 300 - python bench.py
+    run bench_default 300 - python bench.py --full
     for c in cfg3 cfg4 cfg5 ovl250 cfgidx cfg2f64; do
-      run bench_$c 400 - python bench.py --config $c --steps 10 --warmup 2
+      run bench_$c 400 - python bench.py --full --config $c --steps 10 --warmup 2
     done
     ;;
   final2)
     for c in cfg3f64 filt cfg2med cfg2ord sampen256 cfg5m ovl256; do
-      run bench_$c 400 - python bench.py --config $c --steps 10 --warmup 2
+      run bench_$c 400 - python bench.py --full --config $c --steps 10 --warmup 2
     done
     KRE=tile_kernel profile ${P:-r06h}_cfg2 --config cfg2 --plan tile_w256_c3 -- --config cfg2 --steps 10 --warmup 2
     KRE=tile_kernel profile ${P:-r06h}_cfg3 --config cfg3 --plan tile_w256_c1 -- --config cfg3 --steps 5 --warmup 1
