@@ -19,6 +19,7 @@ from . import fft, generic, heart, inertial, util  # noqa: E402,F401
 
 _ALIASES = ("util", "util.windows", "generic", "generic.stats", "generic.timedom",
             "generic.information", "generic.rqa", "generic.frequency", "generic.frequency.density",
+            "generic.frequency.nufft",
             "generic.filters", "heart", "heart.hrv", "heart.qrs", "inertial",
             "inertial.accelerometer", "features", "processing", "fft")
 

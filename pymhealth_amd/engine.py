@@ -453,6 +453,75 @@ def fft(a, direction=_lib.MHF_FFT_FORWARD, scale=1.0, *, stream=None):
     return out
 
 
+def _nufft_device(a, complex_ok):
+    """numpy / torch input -> 1-D contiguous CUDA tensor, float64 (integers, datetime ticks
+    and float32 are widened on the host side of the call) or, for weights, complex128."""
+    if isinstance(a, torch.Tensor):
+        t = a
+    else:
+        a = np.asarray(a)
+        if a.dtype.kind in "mM":
+            a = a.astype(np.int64)
+        t = torch.from_numpy(np.ascontiguousarray(a))
+    if t.dim() != 1:
+        raise ValueError("nufft1d1 takes 1-D arrays")
+    if t.device.type != "cuda":
+        if not torch.cuda.is_available():
+            raise RuntimeError("pymhealth_amd needs an MI355X GPU (torch.cuda.is_available() "
+                               "is False); there is no CPU path")
+        t = t.to("cuda")
+    if t.is_complex():
+        if not complex_ok:
+            raise TypeError("sample positions must be real (got %s)" % t.dtype)
+        return t.to(torch.complex128).contiguous()
+    return t.to(torch.float64).contiguous()
+
+
+def nufft1d1(x, c, starts, ends, M, df=1.0, eps=1e-15, iflag=1, *, min_len=1, power=False,
+             stream=None):
+    """Type-1 non-uniform FFT of the segments ``[starts[b], ends[b])`` of the samples
+    ``(x, c)`` (``mhfx_nufft1d1``, include/mhfeat_nufft.h): row b is the reference's
+    ``nufft1d1(x[s:e], c[s:e], M, df, eps, iflag)``; ``starts = ends = None`` is the one
+    segment of all samples. Returns a ``(B, M)`` CUDA tensor, complex128 or, with
+    ``power``, float64 ``|F|^2``; empty segments and those shorter than ``min_len`` are
+    NaN rows."""
+    from . import _lib_nufft
+    if (starts is None) != (ends is None):
+        raise ValueError("starts and ends must both be given, or both be None")
+    xt = _nufft_device(x, False)
+    ct = _nufft_device(c, True).to(xt.device)
+    if xt.shape[0] != ct.shape[0]:
+        raise ValueError("x and c must have the same length")
+    dev = xt.device
+    if starts is None:
+        st = en = None
+        B = 1
+    else:
+        st, en = (torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v)
+                  .to(device=dev, dtype=torch.int64).reshape(-1).contiguous() for v in (starts, ends))
+        if st.shape[0] != en.shape[0]:
+            raise ValueError("starts and ends must have the same length")
+        B = st.shape[0]
+    M = int(M)
+    out = torch.empty((B, max(M, 0)), dtype=torch.float64 if power else torch.complex128, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    L = _lib_nufft.lib()
+    ws, wsp, wsn = _lib.workspace(L.mhfx_nufft1d1_workspace(M, float(eps), B), dev, stream)
+    with torch.cuda.device(dev):
+        rc = L.mhfx_nufft1d1(
+            ctypes.c_void_p(xt.data_ptr()), ctypes.c_void_p(ct.data_ptr()),
+            _lib_nufft.MHFX_DTYPE_C128 if ct.is_complex() else _lib_nufft.MHFX_DTYPE_F64,
+            xt.shape[0], None if st is None else ctypes.c_void_p(st.data_ptr()),
+            None if en is None else ctypes.c_void_p(en.data_ptr()), B, int(min_len), M,
+            float(df), float(eps), 1 if iflag >= 0 else -1,
+            _lib_nufft.MHFX_OUT_POWER if power else _lib_nufft.MHFX_OUT_COMPLEX,
+            ctypes.c_void_p(out.data_ptr()), max(M, 0), wsp, wsn,
+            _lib.cstream(stream, xt, ct, st, en, out))
+    _lib_nufft.check(rc)
+    del ws
+    return out
+
+
 def plan_name(x_shape_strides, wsize, wstep, feature_ids, out_dtype=torch.float64):
     """Kernel variant the engine would launch (for tests / profiling)."""
     C, cs, ss = x_shape_strides

@@ -1,1 +1,2 @@
 from . import density  # noqa: F401
+from . import nufft  # noqa: F401
