@@ -522,6 +522,113 @@ def nufft1d1(x, c, starts, ends, M, df=1.0, eps=1e-15, iflag=1, *, min_len=1, po
     return out
 
 
+def dfa_step(scale, overlap=0.0):
+    """Step between DFA sub-windows of size ``scale`` at ``overlap`` percent: the reference's
+    ``max(int(w * (100 - overlap) / 100), 1)`` (timedom.py:226), as ``mhfr_dfa_step`` computes
+    it on the host for the launch."""
+    return max(int(int(scale) * (100 - overlap) / 100), 1)
+
+
+def _fractal_inputs(x, starts, ends, what):
+    """(record, starts, ends, n_segments, max_len) for mhfr_dfa / mhfr_hurst: a 1-D float32 /
+    float64 contiguous CUDA record (other dtypes are widened to float64) and int64 bounds on
+    its device. ``max_len`` — the longest clipped segment, which sizes the kernel's LDS — is
+    one reduction on the device and one read-back."""
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+    if t.dim() != 1:
+        raise ValueError("%s takes a 1-D series" % what)
+    if t.is_complex():
+        raise TypeError("%s takes a real series (got %s)" % (what, t.dtype))
+    if t.dtype not in (torch.float32, torch.float64):
+        t = t.to(torch.float64)
+    if t.device.type != "cuda":
+        if not torch.cuda.is_available():
+            raise RuntimeError("pymhealth_amd needs an MI355X GPU (torch.cuda.is_available() "
+                               "is False); there is no CPU path")
+        t = t.to("cuda")
+    t = t.contiguous()
+    n = t.shape[0]
+    if (starts is None) != (ends is None):
+        raise ValueError("starts and ends must both be given, or both be None")
+    if starts is None:
+        return t, None, None, 1, n
+    st, en = (torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v)
+              .to(device=t.device, dtype=torch.int64).reshape(-1).contiguous() for v in (starts, ends))
+    if st.shape[0] != en.shape[0]:
+        raise ValueError("starts and ends must have the same length")
+    B = st.shape[0]
+    if B == 0:
+        return t, st, en, 0, 0
+    # Python slice semantics, as the kernel applies them
+    s = torch.where(st < 0, st + n, st).clamp_(0, n)
+    e = torch.where(en < 0, en + n, en).clamp_(0, n)
+    return t, st, en, B, max(0, int((e - s).max().item()))
+
+
+def _host_i64(values, what):
+    a = np.asarray(values.cpu() if isinstance(values, torch.Tensor) else values)
+    whole = a.dtype.kind in "iu" or (a.dtype.kind == "f" and bool(np.all(a == np.round(a))))
+    if a.ndim != 1 or not whole:
+        raise TypeError("%s must be a 1-D sequence of integers" % what)
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def dfa(x, starts, ends, scales, order=1, overlap=0.0, *, min_len=1, fluctuations=False,
+        stream=None):
+    """Detrended fluctuation analysis of the segments ``[starts[b], ends[b])`` of the record
+    ``x`` (``mhfr_dfa``, include/mhfeat_fractal.h): row b is the reference's
+    ``dfa(x[s:e], scales, order, overlap)`` (timedom.py:196-235); ``starts = ends = None`` is
+    the one segment of all samples. Returns a float64 CUDA tensor, ``(B,)`` exponents or,
+    with ``fluctuations``, ``(B, len(scales))`` values F(w). Segments shorter than
+    ``max(min_len, max(scales))`` (the reference raises) and constant ones are NaN rows;
+    segments beyond ``MHFR_MAX_SEGMENT`` samples raise NotImplementedError."""
+    from . import _lib_fractal
+    t, st, en, B, max_len = _fractal_inputs(x, starts, ends, "dfa")
+    sc = _host_i64(scales, "scales")
+    rows = len(sc) if fluctuations else 1
+    out = torch.empty((B, rows), dtype=torch.float64, device=t.device)
+    stream = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+    L = _lib_fractal.lib()
+    with torch.cuda.device(t.device):
+        rc = L.mhfr_dfa(
+            ctypes.c_void_p(t.data_ptr()),
+            _lib_fractal.MHFR_DTYPE_F64 if t.dtype == torch.float64 else _lib_fractal.MHFR_DTYPE_F32,
+            t.shape[0], None if st is None else ctypes.c_void_p(st.data_ptr()),
+            None if en is None else ctypes.c_void_p(en.data_ptr()), B, int(min_len), max_len,
+            sc.ctypes.data, len(sc), int(order), float(overlap),
+            _lib_fractal.MHFR_OUT_FLUCT if fluctuations else _lib_fractal.MHFR_OUT_EXPONENT,
+            ctypes.c_void_p(out.data_ptr()), rows, _lib.cstream(stream, t, st, en, out))
+    _lib_fractal.check(rc)
+    return out if fluctuations else out[:, 0]
+
+
+def hurst(x, starts, ends, lags=None, *, min_len=1, tau=False, stream=None):
+    """Hurst exponent of the segments ``[starts[b], ends[b])`` of the record ``x``
+    (``mhfr_hurst``): row b is the reference's ``hurst(x[s:e], lags)`` (timedom.py:238-259) on
+    float64 samples, ``lags = None`` its default ``np.arange(2, 64)``. Returns a float64 CUDA
+    tensor, ``(B,)`` exponents or, with ``tau``, ``(B, len(lags))`` values
+    ``sqrt(std(x[l:] - x[:-l]))``. Segments shorter than ``max(min_len, max(lags) + 2)`` and
+    constant ones are NaN rows."""
+    from . import _lib_fractal
+    t, st, en, B, max_len = _fractal_inputs(x, starts, ends, "hurst")
+    lg = _host_i64(np.arange(2, 64) if lags is None else lags, "lags")
+    rows = len(lg) if tau else 1
+    out = torch.empty((B, rows), dtype=torch.float64, device=t.device)
+    stream = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+    L = _lib_fractal.lib()
+    with torch.cuda.device(t.device):
+        rc = L.mhfr_hurst(
+            ctypes.c_void_p(t.data_ptr()),
+            _lib_fractal.MHFR_DTYPE_F64 if t.dtype == torch.float64 else _lib_fractal.MHFR_DTYPE_F32,
+            t.shape[0], None if st is None else ctypes.c_void_p(st.data_ptr()),
+            None if en is None else ctypes.c_void_p(en.data_ptr()), B, int(min_len), max_len,
+            lg.ctypes.data, len(lg),
+            _lib_fractal.MHFR_OUT_FLUCT if tau else _lib_fractal.MHFR_OUT_EXPONENT,
+            ctypes.c_void_p(out.data_ptr()), rows, _lib.cstream(stream, t, st, en, out))
+    _lib_fractal.check(rc)
+    return out if tau else out[:, 0]
+
+
 def plan_name(x_shape_strides, wsize, wstep, feature_ids, out_dtype=torch.float64):
     """Kernel variant the engine would launch (for tests / profiling)."""
     C, cs, ss = x_shape_strides

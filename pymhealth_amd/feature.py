@@ -68,6 +68,87 @@ class WindowFeature:
         return "<WindowFeature %s%s>" % (self.name, extra)
 
 
+class SegmentFeature:
+    """A per-window feature with a launch of its own: one workgroup per window
+    (libmhfeat_fractal.so) instead of an ``mhf_feature`` id of the fused kernel.
+
+    ``kind`` is ``"dfa"`` (params ``windows``, ``o``, ``overlap``) or ``"hurst"`` (param
+    ``lags``, None = the reference's ``np.arange(2, 64)``). Callable on one series like
+    the reference functions (``timedom.hurst(x)``, ``timedom.dfa(x, [4, 8, 16])``); in
+    ``rolling_apply`` bind the parameters with ``functools.partial`` (as for ``sampen``)
+    or take a bound feature from ``features.dfa(windows, o, overlap)``.
+    """
+
+    _SIGNATURES = {"dfa": ("windows", "o", "overlap"), "hurst": ("lags",)}
+
+    def __init__(self, name, kind, ref, doc="", **params):
+        self.name = name
+        self.kind = kind
+        self.params = dict(params)
+        self.__wrapped_ref__ = ref
+        self.__doc__ = "%s [MI355X kernel; reference: %s]\n\n%s" % (name, ref, doc)
+
+    @property
+    def __name__(self):
+        return self.name
+
+    def with_params(self, **params):
+        p = dict(self.params)
+        p.update(params)
+        return SegmentFeature(self.name, self.kind, self.__wrapped_ref__, "", **p)
+
+    def bind(self, args, kwargs):
+        """The reference's positional / keyword arguments after the series."""
+        names = self._SIGNATURES[self.kind]
+        if len(args) > len(names) or set(kwargs) - set(names):
+            raise TypeError("%s(x, %s)" % (self.name, ", ".join(names)))
+        vals = dict(zip(names, args))
+        dup = set(vals) & set(kwargs)
+        if dup:
+            raise TypeError("%s got multiple values for %s" % (self.name, ", ".join(sorted(dup))))
+        vals.update(kwargs)
+        return self.with_params(**vals) if vals else self
+
+    def require_bound(self):
+        if self.kind == "dfa" and self.params.get("windows") is None:
+            raise TypeError("dfa needs its window sizes: pass functools.partial(timedom.dfa, "
+                            "windows=[...]) or features.dfa(windows, o=1, overlap=0)")
+        return self
+
+    def run(self, x, starts, ends, min_len=1):
+        """One launch over the segments ``[starts[b], ends[b])`` of ``x``: a float64 CUDA
+        tensor of one exponent per segment."""
+        from . import engine
+        self.require_bound()
+        p = self.params
+        if self.kind == "dfa":
+            return engine.dfa(x, starts, ends, p["windows"], p.get("o", 1), p.get("overlap", 0.0),
+                              min_len=min_len)
+        return engine.hurst(x, starts, ends, p.get("lags"), min_len=min_len)
+
+    def __call__(self, x, *args, **kwargs):
+        """Evaluate on ONE series (the whole of ``x``), on the GPU. A series too short for
+        the scales / lags gives NaN (the reference raises or returns a non-finite value)."""
+        f = self.bind(args, kwargs)
+        return float(f.run(x, None, None)[0].item())
+
+    def __repr__(self):
+        extra = "" if not self.params else " %s" % self.params
+        return "<SegmentFeature %s%s>" % (self.name, extra)
+
+
+DFA = SegmentFeature(
+    "dfa", "dfa", "timedom.dfa (timedom.py:196-235)",
+    "Detrended fluctuation analysis: the slope of log F(w) against log w, F(w) the mean over "
+    "the sub-windows of scale w of the RMS residual of an order-o polynomial fit of the "
+    "profile cumsum(x - mean(x)). dfa(x, windows, o=1, overlap=0); fp64 (a float32 record is "
+    "widened).", windows=None, o=1, overlap=0)
+HURST = SegmentFeature(
+    "hurst", "hurst", "timedom.hurst (timedom.py:238-259)",
+    "Hurst exponent: 2 x the gradient of o1fit(log lags, log tau), tau = sqrt(std(x[l:] - "
+    "x[:-l])). hurst(x, lags=np.arange(2, 64)); fp64 (numba's float32 chain is not replayed).",
+    lags=None)
+
 _BAND_IDS = (_lib.MHF_BAND_POWER, _lib.MHF_REL_BAND_POWER)
 
 
@@ -243,6 +324,10 @@ def resolve(func):
     """
     if isinstance(func, WindowFeature):
         return func
+    if isinstance(func, SegmentFeature):
+        return func.require_bound()
+    if isinstance(func, functools.partial) and isinstance(func.func, SegmentFeature):
+        return func.func.bind(func.args, dict(func.keywords)).require_bound()
     try:
         if func in _DIRECT:
             return _DIRECT[func]
@@ -264,7 +349,8 @@ def resolve(func):
         "rolling_apply: no MI355X kernel for %r. Supported: np.mean, np.var, np.std, np.min, "
         "np.max, np.median and the "
         "WindowFeature objects of pymhealth_amd.features (stats.skewness, stats.kurtosis, "
-        "timedom.zero_crossing_count, features.rms, features.band_power(fs, lo, hi), ...)."
+        "timedom.zero_crossing_count, features.rms, features.band_power(fs, lo, hi), ...) and "
+        "the SegmentFeatures timedom.hurst / functools.partial(timedom.dfa, windows=[...])."
         % (func,))
 
 

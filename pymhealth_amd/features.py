@@ -119,6 +119,20 @@ def percentile(q):
     return PERCENTILE.with_params(percentile_q=_percentile_q(q))
 
 
+def dfa(windows, o=1, overlap=0):
+    """timedom.dfa(x, windows, o, overlap) of every window (timedom.py:196-235): the DFA
+    scaling exponent. A feature with a launch of its own (libmhfeat_fractal.so), fp64."""
+    from .feature import DFA
+    return DFA.with_params(windows=list(windows), o=int(o), overlap=overlap)
+
+
+def hurst(lags=None):
+    """timedom.hurst(x, lags) of every window (timedom.py:238-259); None = the reference's
+    lags 2 .. 63. A feature with a launch of its own (libmhfeat_fractal.so), fp64."""
+    from .feature import HURST
+    return HURST.with_params(lags=None if lags is None else list(lags))
+
+
 entropy = _ArrayEntropy("entropy", _lib.MHF_ENTROPY, "information.entropy (information.py:10-20)",
                         "Shannon entropy (nats) of x / sum(x) + 1e-30.")
 
@@ -184,7 +198,7 @@ __all__ = ["mean", "var", "std", "skewness", "kurtosis", "kurtosis_excess", "dra
            "percentile", "sampen", "rqa_recurrence_rate", "rqa_determinism",
            "rqa_laminarity", "rqa_length_entropy", "coeff_var", "hjorth_mobility", "hjorth_complexity",
            "rmssd", "sdsd", "ssd", "sdnn", "pnn50", "pnnx", "csi_sd1", "csi_sd2", "lorenz_csi",
-           "lorenz_cvi", "lorenz_mcsi"]
+           "lorenz_cvi", "lorenz_mcsi", "dfa", "hurst"]
 
 
 def extract(x, wsize, wstep, feats, *, out_dtype=None, first_window=0, n_windows=None):

@@ -3,8 +3,15 @@ time-domain per-window features as MI355X WindowFeatures.
 
 ``zero_crossing_count(x, th=0)`` keeps the threshold argument; for rolling_apply bind
 it with ``functools.partial(zero_crossing_count, th=...)`` (rolling_apply passes one
-argument, as in the reference)."""
+argument, as in the reference).
+
+``dfa`` and ``hurst`` are SegmentFeatures (libmhfeat_fractal.so, one workgroup per window):
+``hurst(x)`` / ``dfa(x, [4, 8, 16, 32, 64])`` on one series, or in rolling_apply with the
+parameters bound, ``functools.partial(dfa, windows=[...], o=2, overlap=50)``. Both compute
+in fp64; a float32 series gives the reference's value on ``x.astype(float64)``."""
 import numpy as np
+
+from ..feature import DFA as dfa, HURST as hurst  # noqa: F401
 
 from ..features import (hjorth_activity, hjorth_complexity, hjorth_mobility,  # noqa: F401
                         line_length, zero_crossing_count)
@@ -85,6 +92,56 @@ def hjorth_parameters(x):
     return (v[0], v[1], v[2])
 
 
-__all__ = ["gradient", "zero_crossings", "zero_crossing_count", "line_length",
+def _fit_device(*arrs):
+    """numpy / torch inputs -> float64 CUDA tensors."""
+    import torch
+    out = []
+    for a in arrs:
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+        if t.device.type != "cuda":
+            if not torch.cuda.is_available():
+                raise RuntimeError("pymhealth_amd needs an MI355X GPU (torch.cuda.is_available() "
+                                   "is False); there is no CPU path")
+            t = t.to("cuda")
+        out.append(t.to(torch.float64))
+    return out
+
+
+def _o1fit(x, ys):
+    """Rows (A, b) of the reference's uncentred normal-equation formula (timedom.py:274-279)
+    for every column of ys (n, m), in torch fp64 on the device."""
+    n = x.shape[0]
+    sumx = x.sum()
+    b = ((n * (x[:, None] * ys).sum(0)) - (sumx * ys.sum(0))) / ((n * (x * x).sum()) - (sumx * sumx))
+    A = ys.mean(0) - (b * x.mean())
+    return A, b
+
+
+def o1fit(x, y):
+    """First-order polynomial fit (timedom.py:262-279): ``(A, b)``, intercept and gradient,
+    from the reference's formula as written, in fp64 on the device. Floats for numpy input,
+    0-d tensors for tensor input."""
+    xt, yt = _fit_device(x, y)
+    if xt.dim() != 1 or yt.shape != xt.shape:
+        raise ValueError("o1fit takes two 1-D arrays of one length")
+    A, b = _o1fit(xt, yt[:, None])
+    import torch
+    if isinstance(x, torch.Tensor) or isinstance(y, torch.Tensor):
+        return (A[0], b[0])
+    return (float(A[0].item()), float(b[0].item()))
+
+
+def o1fit_multiple(x, ys):
+    """Fit one line per column of ``ys`` (n, m) on the shared axis ``x`` (timedom.py:282-299):
+    an (m, 2) array of rows (A, b)."""
+    import torch
+    xt, yt = _fit_device(x, ys)
+    if xt.dim() != 1 or yt.dim() != 2 or yt.shape[0] != xt.shape[0]:
+        raise ValueError("o1fit_multiple takes x of shape (n,) and ys of shape (n, m)")
+    out = torch.stack(_o1fit(xt, yt), 1)
+    return out if isinstance(x, torch.Tensor) or isinstance(ys, torch.Tensor) else out.cpu().numpy()
+
+
+__all__ = ["dfa", "hurst", "o1fit", "o1fit_multiple", "gradient", "zero_crossings", "zero_crossing_count", "line_length",
            "hjorth_activity", "hjorth_mobility", "hjorth_complexity",
            "hjorth_mobility_derivative", "hjorth_complexity_derivatives", "hjorth_parameters"]

@@ -35,7 +35,7 @@ from typing import Callable, Dict, List, Optional
 import numpy as np
 from numpy.lib.stride_tricks import as_strided
 
-from ..feature import WindowFeature, plan_groups, resolve
+from ..feature import SegmentFeature, WindowFeature, plan_groups, resolve
 
 
 def view(x: np.ndarray, w: int, s: int) -> np.ndarray:
@@ -86,9 +86,10 @@ def _resolve(func):
     try:
         return resolve(func)
     except TypeError:
-        known = (func is np.percentile or isinstance(func, WindowFeature) or
+        engine_types = (WindowFeature, SegmentFeature)
+        known = (func is np.percentile or isinstance(func, engine_types) or
                  (isinstance(func, functools.partial) and
-                  (func.func is np.percentile or isinstance(func.func, WindowFeature))))
+                  (func.func is np.percentile or isinstance(func.func, engine_types))))
         if known or not callable(func):
             raise
         return UserCallable(func)
@@ -128,17 +129,44 @@ def _run_user(u, arr, wsize, wstep):
     return out
 
 
+def _run_segment(f, arr, wsize, wstep):
+    """A SegmentFeature over the same windows ``arr[i*wstep : i*wstep + wsize]``: ONE launch
+    of its own kernel over all of them (one workgroup per window); float64 like the
+    reference's ``np.zeros((nw,))``."""
+    import torch
+    from ..engine import num_windows, to_device
+    _check_sizes(wsize, wstep)
+    is_torch = isinstance(arr, torch.Tensor)
+    if not is_torch:
+        arr = np.asarray(arr)
+    if arr.ndim == 2:
+        raise TypeError("rolling_apply: %s not defined on 2-D windows (the reference "
+                        "fails on (rows, c) blocks); 2-D input takes %s"
+                        % (f.name, ", ".join(sorted(_BLOCK_FEATURES))))
+    if arr.ndim != 1:
+        raise ValueError("rolling_apply: arr must be 1-D or 2-D")
+    t = to_device(arr, allow_f64=True)
+    nw = num_windows(t.shape[0], wsize, wstep)
+    starts = torch.arange(nw, dtype=torch.int64, device=t.device) * int(wstep)
+    out = f.run(t, starts, starts + int(wsize))
+    return out if is_torch else out.cpu().numpy()
+
+
 def _run(feats, arr, wsize, wstep):
-    """Engine features in fused launches, user callables window by window (_run_user)."""
+    """Engine features in fused launches, each SegmentFeature in one launch of its own
+    (_run_segment), user callables window by window (_run_user)."""
     user = [j for j, f in enumerate(feats) if isinstance(f, UserCallable)]
-    if not user:
+    seg = [j for j, f in enumerate(feats) if isinstance(f, SegmentFeature)]
+    if not user and not seg:
         return _run_native(feats, arr, wsize, wstep)
     _check_sizes(wsize, wstep)
-    native = [j for j in range(len(feats)) if j not in user]
+    native = [j for j in range(len(feats)) if j not in user and j not in seg]
     res = [None] * len(feats)
     if native:
         for j, r in zip(native, _run_native([feats[j] for j in native], arr, wsize, wstep)):
             res[j] = r
+    for j in seg:
+        res[j] = _run_segment(feats[j], arr, wsize, wstep)
     import torch
     for j in user:
         r = _run_user(feats[j], arr, wsize, wstep)
@@ -361,7 +389,8 @@ def _run_indexed(feats, indices, arr, min_window_len):
     if arr.ndim != 1:
         raise ValueError("indices_rolling_apply: arr must be 1-D")
     user = [j for j, f in enumerate(feats) if isinstance(f, UserCallable)]
-    native = [j for j in range(len(feats)) if j not in user]
+    seg = [j for j, f in enumerate(feats) if isinstance(f, SegmentFeature)]
+    native = [j for j in range(len(feats)) if j not in user and j not in seg]
     res = [None] * len(feats)
     if user:
         xh = _host_array(arr)
@@ -371,7 +400,7 @@ def _run_indexed(feats, indices, arr, min_window_len):
         for j in user:
             r = _run_indexed_user(feats[j], ih, xh, int(min_window_len))
             res[j] = torch.from_numpy(r).to(arr.device) if is_torch else r
-    if not native:
+    if not native and not seg:
         return res
     t = to_device(arr, allow_f64=True)
     if isinstance(indices, torch.Tensor):
@@ -381,6 +410,12 @@ def _run_indexed(feats, indices, arr, min_window_len):
         if ind.ndim != 2 or ind.shape[0] != 2:
             raise ValueError("indices must have shape (2, n)")
         ind = torch.from_numpy(np.ascontiguousarray(ind, dtype=np.int64)).to(t.device)
+    if seg and (ind.dim() != 2 or ind.shape[0] != 2):
+        raise ValueError("indices must have shape (2, n)")
+    for j in seg:
+        # one launch of the feature's own kernel over all windows; np.zeros(n, arr.dtype)
+        r = feats[j].run(t, ind[0], ind[1], min_len=int(min_window_len)).to(t.dtype)
+        res[j] = r if is_torch else r.cpu().numpy()
     nfeats = [feats[j] for j in native]
     for idx, kw in plan_groups(nfeats):
         if "fs" in kw:
